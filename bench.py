@@ -90,7 +90,13 @@ def parse():
     ap.add_argument("--probe-only", action="store_true", help=argparse.SUPPRESS)   # only the oracle's logits, nothing timed
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--dp-probe", action="store_true", help=argparse.SUPPRESS)   # sacrificial child of an N > 1 run (run_dp_probe)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its losses, a fixed seeded sample "
+                         "of every module's parameters and gradients) as DIR/<name>.npy, float32")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_baseline_worker(args):
@@ -235,6 +241,35 @@ def pmc_traffic(kernel):
     stamp = blob.get("collected_on", {}).get("csrc_sha16")
     return (round(rec["hbm_bytes_per_launch"]), f"profiles/{os.path.basename(files[-1])} (rocprofv3 --pmc, offline pass)",
             {"csrc_sha16": stamp, "current_csrc_sha16": csrc_sha16(), "stale": stamp != csrc_sha16()})
+
+
+def dump_outputs(path, tr, loss, budget=48 << 20):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy -- the summed loss it returned
+    (`loss`), each loss term (`loss_<term>`), and per optimizer the parameters after its update and the gradients it applied
+    (`params_<module>`, `grads_<module>`).  A buffer longer than its share of `budget` bytes is sampled at fixed positions:
+    one element per equal stretch of the buffer, its place in the stretch drawn from a generator seeded with 0 (the same
+    positions in every run of the same configuration)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss, **{"loss_" + k: v for k, v in tr.losses.items()}}
+    per_buffer = min(1 << 20, budget // 4 // (2 * len(tr.optimizers)))
+    sampled = {}
+    for name, opt in tr.optimizers.items():
+        fp, idx = opt.fp, None
+        if fp.numel > per_buffer:
+            stride = fp.numel // per_buffer
+            jitter = torch.randint(stride, (per_buffer,), generator=torch.Generator().manual_seed(0))
+            idx = (torch.arange(per_buffer) * stride + jitter).to(fp.flat.device)
+            sampled[name] = {"numel": fp.numel, "sampled": per_buffer}
+        for kind, buf in (("params", fp.flat), ("grads", fp.grad)):
+            arrays[f"{kind}_{name}"] = buf if idx is None else buf[idx]
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy())
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": path, "files": sorted(n + ".npy" for n in arrays), "bytes": total, "sampled": sampled}
 
 
 def cpu_baseline(args, probe=None):
@@ -824,9 +859,12 @@ def main():
     GF.SYNC_BN_STATS[:] = [0, 0, 0]
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_loss = step()
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, tr, last_loss)      # before anything else runs a step
     syncbn_per_step = [v // max(1, args.steps) for v in GF.SYNC_BN_STATS]
     rank_ms = None
     if world > 1:
@@ -894,6 +932,8 @@ def main():
                         if tr.merge_passes else False)},
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, probe["path"] if probe else None)
             if probe and os.path.exists(probe["path"] + ".out"):

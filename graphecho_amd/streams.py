@@ -9,12 +9,18 @@ on every stream the new one must run beside, a trivial kernel + event on the can
 its event completes while the spins are still running.  Rejected candidates stay alive (module-level list), so the
 runtime's least-used-queue choice moves on to another queue for the next one.
 """
+import os
 import time
 
 import torch
 
 _REJECTED = []          # streams that aliased a queue we must avoid: kept alive on purpose
 _SPIN_CYCLES = [2_000_000]
+
+
+def hw_queues():
+    """Hardware queues the HIP runtime spreads a process's streams over (GPU_MAX_HW_QUEUES, 4 when unset)."""
+    return int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
 
 
 def _runs_beside(cand, others, device):
@@ -52,6 +58,9 @@ def concurrent_stream(device, beside, tries=8, priority=0):
     serialised)."""
     device = torch.device(device)
     beside = [s for s in beside if s is not None]
+    if len(beside) >= hw_queues():
+        # no hardware queue is left for a stream beside all of them: every candidate would fail its probe
+        return torch.cuda.Stream(device=device, priority=priority)
     first = None
     for _ in range(tries):
         cand = torch.cuda.Stream(device=device, priority=priority)

@@ -7,6 +7,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+if sys.flags.no_user_site:
+    # the child interpreters the tests start (graph cases, data-parallel ranks) skip user site-packages like this one
+    os.environ.setdefault("PYTHONNOUSERSITE", "1")
 
 
 def pytest_configure(config):

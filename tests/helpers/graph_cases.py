@@ -235,7 +235,9 @@ def case_side_streams_run_beside_the_main_stream(dev):
         b = streams.concurrent_stream(dev, [main, a])
         assert a != main and b != main and a != b
         assert streams._runs_beside(a, [main], dev), "the weight-gradient stream shares a hardware queue with the main stream"
-        assert streams._runs_beside(b, [main, a], dev), "GModule's stream shares a hardware queue with a stream it must overlap"
+        # three streams that all run side by side need three hardware queues (GPU_MAX_HW_QUEUES)
+        if streams.hw_queues() >= 3:
+            assert streams._runs_beside(b, [main, a], dev), "GModule's stream shares a hardware queue with a stream it must overlap"
     finally:
         dist.destroy_process_group()
 
